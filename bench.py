@@ -18,6 +18,13 @@ Workloads (BASELINE.json):  N = 1  -> configs[2]: W=200 poses, 50 000 plane feat
                                       iterations/s of that one problem ("scaling": "strong" over N = 2, 4, 8).
                                       --weak keeps 50 000 features per GPU instead.
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, and the roofline figures read off
+the timed steps' own kernel timers).  --full adds every other leg: the natural LM run, the strong-scaling reference, the
+INT8 opt-in, the shipped-window end to end, the CPU baseline (N = 1), the one-GPU run of the same problem and the acceptance
+run against the reference's trace (N > 1).  The --no-* options switch single legs of a --full run off.
+--dump-outputs DIR writes what the last timed LM run handed its caller (balm_damping_iter: poses [W,12], log [iters,8],
+float64) as DIR/poses.npy and DIR/lm_log.npy; the inputs are seeded (--seed), so two builds compare output for output.
 """
 import argparse
 import json
@@ -240,6 +247,13 @@ def cpu_baseline(sc, ctx, target_seconds=20.0):
     }
 
 
+def dump_outputs(d, poses, lm_log):
+    """--dump-outputs DIR: the arrays the timed path's last balm_damping_iter call returned (float64, a few kB)"""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "poses.npy"), np.ascontiguousarray(poses, dtype=np.float64))
+    np.save(os.path.join(d, "lm_log.npy"), np.ascontiguousarray(lm_log, dtype=np.float64))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -306,7 +320,12 @@ def main(argv=None):
     ap.add_argument("--weak", action="store_true", help="N > 1: 50 000 features per GPU instead of 200 000 in total")
     ap.add_argument("--pts", type=int, default=6, help="points per (feature, pose)")
     ap.add_argument("--seed", type=int, default=2024)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the extra legs (cpu_baseline, strong-scaling reference): profiling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the timed loop (natural LM run, strong-scaling reference, INT8, shipped window, CPU baseline; "
+                         "N > 1: one-GPU run of the same problem, acceptance run); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed LM run's outputs (poses.npy, lm_log.npy; float64) to DIR")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the extra legs (cpu_baseline, strong-scaling reference): profiling runs")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-strong-ref", action="store_true",
                     help="N = 1: skip the extra untimed-contract leg that runs configs[3]'s 200 000 features on the one GPU")
@@ -319,6 +338,8 @@ def main(argv=None):
                     help="N > 1: RCCL inside the library (stream-ordered) or the torch.distributed hook")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     from balm_amd import capi, dist as bdist, scene
@@ -351,7 +372,7 @@ def main(argv=None):
     # so that the line carries its own N = 1 point (the other ranks wait in the rendezvous meanwhile)
     one_gpu = None
     sc_full = None
-    if n_gpus > 1 and rank == 0 and not args.no_one_gpu_ref:
+    if n_gpus > 1 and rank == 0 and args.full and not args.no_one_gpu_ref:
         try:
             sc_full = scene.generate(args.seed, W, Fg * n_gpus, args.pts, mode=1, feature_offset=0)
             one_gpu = one_gpu_same_problem(sc_full, W, local_rank)
@@ -390,14 +411,17 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    # the natural LM run first (untimed region of the contract; reported as its own figure): from the noisy start to
+    # --full: the natural LM run first (untimed region of the contract; reported as its own figure): from the noisy start to
     # the reference's own stop rule, benchmark_virtual.cpp's constants
-    H_first = ctx.evaluate(0, sc.poses_init)[0]    # (the process's first device work -- code objects, buffers -- is not the run's)
-    barrier()
-    t0 = time.perf_counter()
-    poses_nat, lg_nat = ctx.damping_iter(sc.poses_init, form=0, u0=0.1, max_iter=20)
-    barrier()
-    t_nat = time.perf_counter() - t0
+    t_nat = 0.0
+    if args.full:
+        H_first = ctx.evaluate(0, sc.poses_init)[0]    # (the process's first device work -- code objects, buffers -- is not the run's)
+        barrier()
+        t0 = time.perf_counter()
+        poses_nat, lg_nat = ctx.damping_iter(sc.poses_init, form=0, u0=0.1, max_iter=20)
+        barrier()
+        t_nat = time.perf_counter() - t0
+    last = {}
 
     def run_steps(k, ctx=ctx):
         """exactly k LM iterations, in runs of at most 20 from the noisy start (a run that sat at the optimum for hundreds
@@ -405,10 +429,11 @@ def main(argv=None):
         logs = []
         while k > 0:
             m = min(20, k)
-            _, lg_ = ctx.damping_iter(sc.poses_init, form=0, u0=0.1, max_iter=m, force_hess=True, no_stop=True, reanchor=False)
+            poses_, lg_ = ctx.damping_iter(sc.poses_init, form=0, u0=0.1, max_iter=m, force_hess=True, no_stop=True, reanchor=False)
             assert len(lg_) == m
             logs.append(lg_)
             k -= m
+        last["poses"], last["log"] = poses_, lg_         # what the last damping_iter call handed its caller
         return np.concatenate(logs)
 
     if args.warmup > 0:
@@ -420,6 +445,7 @@ def main(argv=None):
     barrier()
     dt = time.perf_counter() - t0
     assert len(lg) == args.steps
+    timed_out = dict(last)
     if multi:
         import torch.distributed as dist
         tt = torch.tensor([dt, t_nat], dtype=torch.float64, device="cuda")
@@ -430,7 +456,7 @@ def main(argv=None):
     wm = ctx.work_model()
     comm = ctx.comm_info()
     accept = None
-    if (multi or inproc) and not args.no_accept:
+    if (multi or inproc) and args.full and not args.no_accept:
         accept = acceptance_check(ctx, sc.poses_init, args.seed, W, Fg * n_gpus, args.pts)
     if multi:
         import torch.distributed as dist
@@ -440,6 +466,8 @@ def main(argv=None):
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed_out["poses"], timed_out["log"])
 
     F_total = Fg * n_gpus
     iters_per_s = args.steps / dt
@@ -522,7 +550,7 @@ def main(argv=None):
         "kernel_ms_per_step": per_step,
         "roofline": roofline,
         "roofline_secondary": secondary,
-        "natural_lm_run": {"what": "damping_iter from the noisy start to the reference's stop rule (u0=0.1, <=20 iterations), "
+        "natural_lm_run": None if not args.full else {"what": "damping_iter from the noisy start to the reference's stop rule (u0=0.1, <=20 iterations), "
                                    "Hessian re-evaluated only after accepted steps; includes the pose upload/download; warm (one evaluation ran before it)",
                            "iterations": int(len(lg_nat)), "ms_total": t_nat * 1e3,
                            "iterations_per_sec": len(lg_nat) / t_nat, "final_residual": float(lg_nat[-1, 1])},
@@ -539,7 +567,7 @@ def main(argv=None):
     if n_gpus > 1:
         out["one_gpu_same_problem"] = one_gpu
         out.update(scaling_fields(iters_per_s, one_gpu if one_gpu and "error" not in one_gpu else None, n_gpus))
-    if n_gpus > 1 and out["scaling"] == "strong" and F_total == F_SHARDED_TOTAL and os.path.exists(N1_TRACE):
+    if n_gpus > 1 and args.full and out["scaling"] == "strong" and F_total == F_SHARDED_TOTAL and os.path.exists(N1_TRACE):
         # `value` at N = 1 is configs[2] (50 000 features), a 4x smaller problem than the one sharded here: the N = 1 point of THIS curve is the
         # same 200 000-feature problem on one GPU, measured by the N = 1 bench run (strong_scaling_reference) and committed with its LM trace
         try:
@@ -551,7 +579,7 @@ def main(argv=None):
                                                             "speedup_of_this_run": iters_per_s / t1["iterations_per_sec"]}
         except Exception:
             pass
-    if n_gpus == 1 and not multi and not args.no_strong_ref and not args.no_cpu and args.features == 0 and W == 200:      # (--no-cpu: no extra legs at all)
+    if n_gpus == 1 and not multi and args.full and not args.no_strong_ref and not args.no_cpu and args.features == 0 and W == 200:      # (--no-cpu: no extra legs at all)
         # the problem the N > 1 runs shard (BASELINE configs[3]: 200 000 features in total) on ONE GPU: the N = 1 point of the
         # strong-scaling curve (`value` above is configs[2], a 4x smaller problem, and not comparable with the N > 1 values)
         try:
@@ -609,7 +637,7 @@ def main(argv=None):
             ctx.set_features(sc.clusters, None, sc.coeffs)
         except Exception as e:
             out["strong_scaling_reference"] = {"error": repr(e)}
-    if n_gpus == 1 and not multi and not args.no_cpu and not args.no_int8:
+    if n_gpus == 1 and not multi and args.full and not args.no_cpu and not args.no_int8:
         # BALM_SYRK=int8 (opt-in): the same workload, the same timed loop, K3 on the INT8 matrix cores by error-free slicing.  An
         # EXTRA key: `value`, `dtype` and `roofline` above are the default FP64 path's.
         try:
@@ -655,7 +683,7 @@ def main(argv=None):
             os.environ.pop("BALM_SYRK", None)
             ctx = capi.Context(W, local_rank, capi.FLAG_TIMING)
             ctx.set_features(sc.clusters, None, sc.coeffs)
-    if n_gpus == 1 and not multi and not args.no_cpu and not args.no_realworld:
+    if n_gpus == 1 and not multi and args.full and not args.no_cpu and not args.no_realworld:
         # the path the reference ships data for (benchmark_realworld.cpp:183-218), end to end from host memory; an extra key,
         # outside the timed region of `value`
         from balm_amd import realworld as rw
@@ -680,7 +708,7 @@ def main(argv=None):
                 out["realworld_end_to_end"] = {"error": repr(e)}
         else:
             out["realworld_end_to_end"] = {"skipped": "datasets/realworld_w177.npz not present (tools/make_realworld_fixture.py writes it where the shipped data exists)"}
-    if n_gpus == 1 and not args.no_cpu:
+    if n_gpus == 1 and args.full and not args.no_cpu:
         try:
             out["cpu_baseline"] = cpu_baseline(sc, ctx, args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]

@@ -27,3 +27,5 @@ g++ -std=c++14 -O2 -w -pthread -I"$ROOT/oracle/compat" -I"$REF/include" -I"$REF/
     -o "$ROOT/tools/bin/shim_realworld_e2e" "$ROOT/tests/cpp/shim_realworld_e2e.cpp" \
     -L"$ROOT/balm_amd/lib" -lbalm_hip -ldl -Wl,-rpath,'$ORIGIN/../../balm_amd/lib'
 echo "built $ROOT/tools/bin/shim_realworld_e2e"
+# the tests' copy, beside the fixtures it is checked against (oracle/_ref travels with them)
+cp "$ROOT/tools/bin/shim_realworld_e2e" "$ROOT/oracle/_ref/shim_realworld_e2e"

@@ -50,6 +50,14 @@ def test_scaling_fields_of_an_n_gpu_line():
     assert abs(bench.COMM_MODEL_MS - 0.10) < 1e-12
 
 
+def test_full_and_dump_outputs_options():
+    """--full and --dump-outputs are part of the command line; --steps below 1 is refused before any device work"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = _run(["--steps", "0"])
+    assert p.returncode == 2 and "--steps" in p.stderr
+
+
 @pytest.mark.skipif(__import__("torch").cuda.is_available(), reason="CPU-box behaviour")
 def test_gpus_2_without_a_gpu_says_no_gpu():
     p = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"])
@@ -71,7 +79,7 @@ def test_gpus_2_on_a_one_gpu_box_reaches_the_device_count_check():
 def test_one_process_fallback_runs_two_loopback_shards():
     """the balm_create_multi leg of bench.py (what runs if torch.distributed.run cannot start), on one device"""
     import json
-    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--features", "1500", "--win", "40", "--no-cpu", "--no-accept"],
+    p = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--features", "1500", "--win", "40", "--full", "--no-cpu", "--no-accept"],
              {"BALM_BENCH_LOOPBACK": "1"})
     assert p.returncode == 0, p.stderr[-2000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
@@ -85,3 +93,28 @@ def test_one_process_fallback_runs_two_loopback_shards():
     assert abs(d["speedup_vs_one_gpu_same_problem"] - d["value"] / one["iterations_per_sec"]) < 1e-9
     assert abs(d["scaling_efficiency"] - d["speedup_vs_one_gpu_same_problem"] / 2) < 1e-12
     assert d["comm"]["allreduce_ms_per_step"] > 0 and d["comm"]["model_ms_per_step_assumed"] == 0.1
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """a plain run: exactly --steps timed steps, none of the --full legs, and --dump-outputs writes the last timed LM run's
+    poses and log; the seeded inputs make a second run's outputs the same"""
+    import json
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        p = _run(["--steps", "3", "--warmup", "1", "--features", "1500", "--win", "40", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+        for key in ("cpu_baseline", "int8_syrk", "realworld_end_to_end", "strong_scaling_reference"):
+            assert key not in line
+        assert line["natural_lm_run"] is None
+        poses, lg = np.load(d / "poses.npy"), np.load(d / "lm_log.npy")
+        assert poses.dtype == np.float64 and poses.shape == (40, 12) and np.all(np.isfinite(poses))
+        assert lg.dtype == np.float64 and lg.shape == (3, 8) and np.all(lg[:, 7] == 1)      # every timed step re-evaluates the Hessian
+        assert abs(lg[-1, 1] - line["final_residual"]) <= 1e-12 * abs(line["final_residual"])
+        outs.append((poses, lg))
+    assert np.allclose(outs[0][0], outs[1][0], rtol=1e-9, atol=1e-12)
+    assert np.allclose(outs[0][1][:, :2], outs[1][1][:, :2], rtol=1e-9, atol=0)

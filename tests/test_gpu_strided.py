@@ -157,10 +157,12 @@ def test_cpp_shim_on_the_shipped_window_installs_the_references_feature_set(tmp_
     from balm_amd import realworld as rw
     from test_association import canon
     ff = os.path.join(ROOT, "oracle", "_ref", "realworld_features.npz")
-    if not (os.path.exists(rw.CPP_E2E_EXE) and os.path.exists(rw.SHIPPED_WINDOW_NPZ) and os.path.exists(ff)):
-        pytest.skip("tools/bin/shim_realworld_e2e / datasets/realworld_w177.npz / oracle/_ref/realworld_features.npz not built")
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim_realworld_e2e")              # tests/cpp/build_shim_driver.sh's copy of tools/bin's
+    win = os.path.join(ROOT, "oracle", "_ref", "realworld_scans_w177.npz")        # the file datasets/realworld_w177.npz links to
+    if not (os.path.exists(exe) and os.path.exists(win) and os.path.exists(ff)):
+        pytest.skip("oracle/_ref/shim_realworld_e2e / realworld_scans_w177.npz / realworld_features.npz not built")
     feats = str(tmp_path / "features.bin")
-    res = rw.end_to_end_cpp(reps=2, features_out=feats)
+    res = rw.end_to_end_cpp(win, reps=2, exe=exe, features_out=feats)
     assert res["vs_reference"]["ok"], res
     ref = np.load(ff)
     raw = np.fromfile(feats, dtype=np.float64)

@@ -8,8 +8,8 @@
 REPO=$(pwd); TAG=${TAG:-r06z}; OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp PYTHONPATH=$REPO
 timeout 1800 python -m pytest tests -q -m gpu > $OUT/pytest_gpu.txt 2>&1 < /dev/null; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu.txt; tail -3 $OUT/pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 < /dev/null; echo "smoke rc=$?"; tail -2 $OUT/smoke.txt
-timeout 2400 bash tools/gpu_profile_round.sh $TAG < /dev/null
-BALM_BENCH_LOOPBACK=1 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 1 --no-cpu 2>/dev/null | grep "^{" > $OUT/bench_loopback2.json; echo "loopback bench rc=$?"
+timeout 2400 bash tools/gpu_profile_round.sh $TAG $OUT < /dev/null
+BALM_BENCH_LOOPBACK=1 timeout 600 python bench.py --gpus 2 --steps 5 --warmup 1 --full --no-cpu 2>/dev/null | grep "^{" > $OUT/bench_loopback2.json; echo "loopback bench rc=$?"
 timeout 300 python tools/bench_upload.py 2>&1 | grep -v amdgpu.ids > $OUT/uploads.txt; cut -c1-200 $OUT/uploads.txt | grep -v shipped
 timeout 600 python tools/bench_upload.py --shards 8 2>&1 | grep -v amdgpu.ids | tee $OUT/upload_shards8.txt
 timeout 300 python tools/bench_voxel.py --real --no-cpu 2>&1 | grep -v amdgpu.ids | tee $OUT/voxel.txt
